@@ -12,7 +12,7 @@ objective+gradient evaluation budget (--evals, default 20; SURVEY.md 8(d) "fixed
 (`eval_cap`): with scipy's `maxfun` alone a run overshoots by up to a line search, and the total then moves by
 +-8 % with the last bits of the arithmetic (173 vs 188 evaluations between two versions of one kernel).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
 
 N > 1 is one process per GPU.  Under a launcher (torch.distributed.run exports RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_*) this process IS one rank.  Started as a plain process with --gpus N > 1 it is the launcher: before anything
@@ -27,6 +27,8 @@ N > 1 is STRONG scaling of the same job: the randomized restarts and the N* pred
 ranks (sharding.py: rendezvous + tiny object gathers over TCP, device collectives = RCCL inside libmfgp_hip.so; no
 PyTorch anywhere); rank 0 alone runs the sequential first HF run -> restart 0.
 Prints ONE JSON line on rank 0.  `value` = milliseconds per fit+predict (lower is better).
+--dump-outputs DIR writes what the last timed step returned -- the posterior mean and variance at the N* test points -- as
+DIR/mean.npy and DIR/var.npy (float64); the inputs are fixed by the arguments, so two builds can be compared array by array.
 The CPU comparator (`cpu_baseline`) is the numpy/LAPACK oracle timed on the host cores of the same box
 on a bounded sample (one objective+gradient evaluation per level + the predict products), scaled by the
 number of evaluations the GPU path actually issued.
@@ -400,6 +402,23 @@ def sharding_note(world, restarts, rccl_ranks):
                else " alone (every other rank has restarts of its own)"))
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: arrays (equal numbers of rows) -> out_dir/<name>.npy as float64.  Above DUMP_LIMIT_BYTES in all, the same
+    fixed, seeded sample of rows (in their original order) is written for every array."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    rows = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // max(len(a), 1) for a in arrays.values())
+    keep = None
+    if rows * row_bytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(seed).choice(rows, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if keep is None else a[keep])
+
+
 def launch_ranks(n_ranks, argv, script=None):
     """the --gpus N > 1 job started as a plain process: N child processes of this script, one rank per GPU.  Runs BEFORE
     this process imports the engine or touches HIP (it never does).  Children inherit stdout / stderr, so rank 0's JSON
@@ -487,7 +506,12 @@ def main():
     ap.add_argument("--single-device", action="store_true",
                     help="rehearsal only: every rank uses GPU 0; RCCL is made to accept that by giving every rank its own "
                          "NCCL_HOSTID (a real N-rank communicator over RCCL's socket transport on loopback)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (posterior mean and variance at the N* test "
+                         "points) as DIR/<name>.npy, float64 (rank 0 only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))     # nothing below runs in the launcher; no HIP call was made
@@ -591,6 +615,8 @@ def main():
     wall1 = time.time()
     power = stop_power_watch(power_proc, wall0, wall1) if power_proc is not None else None
     ms_per_step = dt * 1e3 / args.steps
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"mean": mean, "var": var})
 
     # outside the timed region: the row-block K build + RCCL all-gather layout of north_star,
     # one evaluation each way on the HF level, reported next to the local build it competes with

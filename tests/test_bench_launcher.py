@@ -72,3 +72,31 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True, text=True,
                        timeout=120, env=env)
     assert r.returncode == 2 and "WORLD_SIZE=3" in r.stderr
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one DIR/<name>.npy per array, float64; above the limit the same seeded rows of every array"""
+    import bench
+    mean = np.arange(1000.0)[:, None]
+    var = 2.0 * mean
+    bench.dump_outputs(str(tmp_path / "all"), {"mean": mean, "var": var.astype(np.float32)})
+    got = {n: np.load(str(tmp_path / "all" / (n + ".npy"))) for n in ("mean", "var")}
+    assert sorted(os.listdir(str(tmp_path / "all"))) == ["mean.npy", "var.npy"]
+    assert got["mean"].dtype == got["var"].dtype == np.float64
+    np.testing.assert_array_equal(got["mean"], mean)
+    np.testing.assert_array_equal(got["var"], var)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1600)          # 100 rows of (mean, var)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"mean": mean, "var": var})
+    s1 = {n: np.load(str(tmp_path / "s1" / (n + ".npy"))) for n in ("mean", "var")}
+    s2 = {n: np.load(str(tmp_path / "s2" / (n + ".npy"))) for n in ("mean", "var")}
+    assert s1["mean"].shape == (100, 1) and sum(a.nbytes for a in s1.values()) <= 1600
+    np.testing.assert_array_equal(s1["var"], 2.0 * s1["mean"])                # the same rows of both arrays
+    assert np.all(np.diff(s1["mean"][:, 0]) > 0)                              # in their original order
+    for n in ("mean", "var"):
+        np.testing.assert_array_equal(s1[n], s2[n])                            # and the same rows every time
+
+
+def test_bench_refuses_zero_timed_steps():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr and '"metric"' not in r.stdout
